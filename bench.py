@@ -12,6 +12,14 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run only sets up, warms up, times the K rounds and prints one JSON
+result line. `--dump-outputs DIR` additionally writes what the last timed
+round returned to its caller (aggregated server parameters + aggregated fit
+metrics) as DIR/<name>.npy, so two builds can be compared output for output;
+inputs are fully seeded and identical from run to run. `--full` is reserved
+for extra measurements beyond the headline figure; the benchmark has none
+today, so it changes nothing.
 """
 from __future__ import annotations
 
@@ -34,6 +42,8 @@ from fl4health_amd.strategies.fedavg_with_adaptive_constraint import FedAvgWithA
 from fl4health_amd.utils.random import set_all_random_seeds
 
 log = logging.getLogger("bench")
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
 
 
 class BenchFedProxClient(FedProxClient):
@@ -115,6 +125,34 @@ def make_strategy(args: argparse.Namespace, device: torch.device) -> FedAvgWithA
     )
 
 
+def dump_outputs(out_dir: str, fit_result) -> None:
+    """Write what the last timed `fit_round` returned to its caller as
+    <out_dir>/<name>.npy: the aggregated server parameters (fp32) and every
+    numeric aggregated fit metric (fp64 scalars). An output that would push
+    the total past DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    params, metrics, _ = fit_result
+    arrays: dict[str, "np.ndarray"] = {}
+    for i, t in enumerate(params.tensors):
+        arrays[f"server_params_{i}"] = t.detach().to("cpu", torch.float32).contiguous().numpy()
+    for key in sorted(metrics or {}):
+        v = metrics[key]
+        if isinstance(v, torch.Tensor):
+            arrays[f"fit_metric_{key}"] = v.detach().to("cpu", torch.float64).numpy()
+        elif isinstance(v, (bool, int, float)):
+            arrays[f"fit_metric_{key}"] = np.asarray(float(v), dtype=np.float64)
+    budget = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            keep = max(budget // max(a.itemsize, 1), 0)
+            idx = np.sort(np.random.default_rng(20240607).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
@@ -129,6 +167,10 @@ def main() -> None:
                         help="use the hand-written MFMA direct 3x3 conv (CdnaConv2d) instead of MIOpen (default on)")
     parser.add_argument("--no_cdna_conv", dest="cdna_conv", action="store_false",
                         help="fall back to MIOpen for the 3x3 convs")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed rounds, write the last round's outputs to DIR/<name>.npy")
+    parser.add_argument("--full", action="store_true",
+                        help="also run measurements beyond the headline figure (none today: no-op)")
     args = parser.parse_args()
 
     set_all_random_seeds(42)
@@ -157,18 +199,25 @@ def main() -> None:
             server.client_manager.register(RankClientProxy(str(cid), runtime))
         server._get_initial_parameters(None)
 
-        def one_round(r: int) -> None:
+        def one_round(r: int):
             server.current_round = r
-            server.fit_round(r, None)
+            return server.fit_round(r, None)
 
         for r in range(1, args.warmup + 1):
             one_round(r)
         runtime.bench_sync()
         runtime.bench_mark()
-        for r in range(args.warmup + 1, args.warmup + args.steps + 1):
-            one_round(r)
+        last = None
+        final = args.warmup + args.steps
+        for r in range(args.warmup + 1, final + 1):
+            out = one_round(r)
+            if r == final and args.dump_outputs:
+                last = out  # keep only the last timed round's return value
+            del out
         runtime.bench_sync()
         elapsed = runtime.bench_elapsed_max()
+        if last is not None:
+            dump_outputs(args.dump_outputs, last)
 
         ms_per_round = elapsed / args.steps * 1000.0
         samples_per_round = world * args.local_steps * args.batch_size

@@ -8,6 +8,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+from tests.test_utils import NO_GPU, two_rank_env
+
 ROOT = Path(__file__).resolve().parent.parent
 
 WORKER = r"""
@@ -352,7 +354,7 @@ def test_bench_script_two_rank_contract(tmp_path):
     """bench.py's driver contract at N=2 (the SCALE run path): torchrun two
     ranks over gloo, rank 0 prints exactly one JSON line with the required
     fields and whole-job aggregate value."""
-    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    env = two_rank_env()
     out = subprocess.run(
         [
             sys.executable, "-m", "torch.distributed.run",
@@ -682,7 +684,9 @@ def test_fsdp_actually_shards_at_world_two(tmp_path):
     full parameters back."""
     script = tmp_path / "fsdp_worker.py"
     script.write_text(FSDP_WORKER)
-    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    # the worker is a gloo group over CPU tensors; with a GPU in sight
+    # shard_model would build a cuda mesh under it, so keep the child CPU-only
+    env = dict(os.environ, PYTHONPATH=str(ROOT), **NO_GPU)
     out = subprocess.run(
         [
             sys.executable, "-m", "torch.distributed.run",
@@ -703,7 +707,8 @@ def test_bench_script_single_rank_contract(tmp_path):
     env = dict(os.environ, PYTHONPATH=str(ROOT))
     out = subprocess.run(
         [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
-         "--shard_size", "256", "--batch_size", "32"],
+         "--shard_size", "256", "--batch_size", "32",
+         "--full", "--dump-outputs", str(tmp_path / "dump")],
         capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT),
     )
     assert out.returncode == 0, out.stderr[-2000:]
@@ -721,3 +726,18 @@ def test_bench_script_single_rank_contract(tmp_path):
     assert rec["dtype"] in ("bf16", "fp32") and "synthetic" in rec["data"]
     assert rec["value"] > 0 and rec["ms_per_step"] > 0
     assert isinstance(rec["config"], dict) and "model" in rec["config"]
+    # --dump-outputs: the last timed round's outputs as float .npy files,
+    # at most 64 MB in all, holding the aggregated flat parameter vector
+    import numpy as np
+
+    from fl4health_amd.models.resnet import ResNet18
+    from fl4health_amd.parameter_exchange.flat import FlatParameterView
+
+    dumped = sorted((tmp_path / "dump").glob("*.npy"))
+    assert dumped, "no outputs dumped"
+    arrays = {p.stem: np.load(p) for p in dumped}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1024 * 1024
+    flat = arrays["server_params_0"]
+    assert flat.shape == (FlatParameterView(ResNet18(num_classes=10)).flat.numel(),)
+    assert np.isfinite(flat).all() and np.abs(flat).max() > 0

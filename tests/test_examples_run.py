@@ -6,6 +6,8 @@ from pathlib import Path
 
 import pytest
 
+from tests.test_utils import two_rank_env
+
 ROOT = Path(__file__).resolve().parent.parent
 
 EXAMPLES = [
@@ -50,7 +52,7 @@ def test_heavy_workload_example_runs(name):
 def test_heavy_workload_torchrun_two_ranks(name):
     """BASELINE heavy configs must run the one-rank-per-GPU path (gloo in CI;
     RCCL on hardware) via the standard torchrun launcher."""
-    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    env = two_rank_env()
     port = "29561" if "bert" in name else "29563"
     out = subprocess.run(
         [

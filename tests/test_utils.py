@@ -2,6 +2,9 @@
 + custom_client_proxy.py)."""
 from __future__ import annotations
 
+import os
+from pathlib import Path
+
 import torch
 import torch.nn as nn
 
@@ -9,6 +12,20 @@ from fl4health_amd.clients.basic_client import BasicClient
 from fl4health_amd.datasets.synthetic import synthetic_cifar_loaders
 from fl4health_amd.metrics.metrics import Accuracy
 from fl4health_amd.optimizers import FlatProxSGD
+
+
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
+
+def two_rank_env() -> dict:
+    """Environment for a two-rank torchrun child of an entry point that puts
+    one rank on each GPU whenever it sees a GPU. That needs two devices; on a
+    machine that shows just one, hide it so both ranks take the CPU/gloo path
+    (what a machine without a GPU runs) instead of fighting over ordinal 0."""
+    env = dict(os.environ, PYTHONPATH=str(Path(__file__).resolve().parent.parent))
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env.update(NO_GPU)
+    return env
 
 
 class TinyNet(nn.Module):
