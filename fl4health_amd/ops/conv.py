@@ -16,6 +16,8 @@ shapes/devices fall back to F.conv2d.
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as Fn
@@ -77,22 +79,34 @@ def _variant_for(width: int, c: int, k: int) -> str | None:
     return None
 
 
-def _use_kb32(width: int, c: int, k: int) -> bool:
-    return _variant_for(width, c, k) is not None
+@functools.lru_cache(maxsize=None)
+def _both_directions_fit(n: int, h: int, w: int, c: int, k: int) -> bool:
+    """The kernels' checked launch plan (csrc/conv_plan.h) for the real
+    N, H, W: the forward conv C->K and the backward-data conv K->C must both
+    fit the LDS carve-up of the kernel each would run (the adopted variant,
+    else whatever conv3x3_fwd picks)."""
+    return all(
+        _C.conv3x3_plan(_variant_for(w, ci, ko) or "fwd", n, h, w, ci, ko)["fits"]
+        for ci, ko in ((c, k), (k, c))
+    )
+
+
+def _is_3x3_s1p1(m: nn.Conv2d) -> bool:
+    """The one conv the kernels implement: 3x3, stride 1, zero pad 1, dense."""
+    return (
+        m.kernel_size == (3, 3)
+        and m.stride == (1, 1)
+        and m.padding == (1, 1)
+        and m.dilation == (1, 1)
+        and m.groups == 1
+        and m.padding_mode == "zeros"  # kernel hardcodes zero halo
+    )
 
 
 def _run_variant(variant: str, x_nhwc: torch.Tensor, wimg: torch.Tensor, bias):
     if variant == "kzloop":
         return _C.conv3x3_fwd_kzloop(x_nhwc, wimg, bias)
     return _C.conv3x3_fwd_kb32(x_nhwc, wimg, bias)
-
-
-def _run_fwd(x_nhwc: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor | None) -> torch.Tensor:
-    width, c, k = x_nhwc.shape[2], w9.shape[1], w9.shape[2]
-    variant = _variant_for(width, c, k)
-    if variant is not None:
-        return _run_variant(variant, x_nhwc, _image_kb32(w9), bias)
-    return _C.conv3x3_fwd(x_nhwc, w9, bias)
 
 
 class _CdnaConv3x3Fn(torch.autograd.Function):
@@ -107,7 +121,7 @@ class _CdnaConv3x3Fn(torch.autograd.Function):
                 bias.float() if bias is not None else None,
             )
         else:
-            y = _run_fwd(x_nhwc, _pack_fwd(w16), bias.float() if bias is not None else None)
+            y = _C.conv3x3_fwd(x_nhwc, _pack_fwd(w16), bias.float() if bias is not None else None)
         ctx.save_for_backward(x_nhwc, w16)
         ctx.has_bias = bias is not None
         return y
@@ -123,7 +137,7 @@ class _CdnaConv3x3Fn(torch.autograd.Function):
         if bwd_variant is not None:
             dx = _run_variant(bwd_variant, gy, _C.pack_kb32(w16.contiguous(), True), None)
         else:
-            dx = _run_fwd(gy, _pack_bwd(w16), None)
+            dx = _C.conv3x3_fwd(gy, _pack_bwd(w16), None)
         # dW: route to MIOpen's tuned wrw igemm. The round-1 "9 shifted
         # GEMMs" form ran fp32 rocBLAS (no matrix cores) and measured 316 ms
         # of a 450 ms steady-state window (gpurun_out/cdna_bench_kernels.md);
@@ -193,7 +207,7 @@ class CdnaConv2d(nn.Conv2d):
     fast path (CPU, fp32 eval, unsupported widths, other hyper-params).
 
     Adoption is gated per shape to where a kernel variant MEASURES faster
-    than TUNED MIOpen (cudnn.benchmark find; see _use_kb32): the KB=32
+    than TUNED MIOpen (cudnn.benchmark find; see _variant_for): the KB=32
     fully-pipelined kernel at 4x4 C512 (1.23x) and 8x8 C<=128 (1.50x). The
     other variants (8-wave persistent-weight glds at 32x32, round-1 direct
     at 16x16) beat MIOpen's *default* solver picks by 1.2-1.9x but lose to
@@ -202,25 +216,18 @@ class CdnaConv2d(nn.Conv2d):
     force_mfma: bool = False  # True: run our kernels on every supported width
 
     def _fast_path(self, input: torch.Tensor) -> bool:
-        ok = (
-            HAS_EXT
-            and input.is_cuda
-            and input.dtype == torch.bfloat16
-            and self.kernel_size == (3, 3)
-            and self.stride == (1, 1)
-            and self.padding == (1, 1)
-            and self.dilation == (1, 1)
-            and self.groups == 1
-            and self.padding_mode == "zeros"  # kernel hardcodes zero halo
-        )
-        if not ok:
+        if not (HAS_EXT and input.is_cuda and input.dtype == torch.bfloat16 and _is_3x3_s1p1(self)):
             return False
+        n, _, h, w = input.shape
+        c, k = self.in_channels, self.out_channels
         if self.force_mfma:
-            return input.shape[3] <= 32
-        # both conv directions must hit the measured-win kb32 shapes
-        return _use_kb32(input.shape[3], self.in_channels, self.out_channels) and _use_kb32(
-            input.shape[3], self.out_channels, self.in_channels
-        )
+            adopted = w <= 32
+        else:
+            # both conv directions must hit the measured-win shapes
+            adopted = _variant_for(w, c, k) is not None and _variant_for(w, k, c) is not None
+        # ... and the real N, H, W must fit the kernels' LDS (small images
+        # pack many samples per tile and can overflow it)
+        return adopted and _both_directions_fit(n, h, w, c, k)
 
     def _wrw_path(self, input: torch.Tensor) -> bool:
         """MIOpen fwd/dx + custom MFMA wrw: measured win at 32x32 C64->K64
@@ -235,12 +242,7 @@ class CdnaConv2d(nn.Conv2d):
             and input.dtype == torch.bfloat16
             and self.weight.dtype == torch.bfloat16
             and self.bias is None
-            and self.kernel_size == (3, 3)
-            and self.stride == (1, 1)
-            and self.padding == (1, 1)
-            and self.dilation == (1, 1)
-            and self.groups == 1
-            and self.padding_mode == "zeros"
+            and _is_3x3_s1p1(self)
             and self.in_channels == 64
             and self.out_channels == 64
             and input.shape[3] == 32
@@ -265,14 +267,6 @@ def convert_conv3x3_to_cdna(model: nn.Module) -> nn.Module:
     """Class-swap every eligible nn.Conv2d to CdnaConv2d (state_dict
     compatible; same pattern as convert_batchnorm_to_cdna)."""
     for _name, m in model.named_modules():
-        if (
-            type(m) is nn.Conv2d
-            and m.kernel_size == (3, 3)
-            and m.stride == (1, 1)
-            and m.padding == (1, 1)
-            and m.dilation == (1, 1)
-            and m.groups == 1
-            and m.padding_mode == "zeros"
-        ):
+        if type(m) is nn.Conv2d and _is_3x3_s1p1(m):
             m.__class__ = CdnaConv2d
     return model

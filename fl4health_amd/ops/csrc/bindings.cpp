@@ -4,6 +4,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include "conv_plan.h"
+
 extern "C" {
 void launch_axpby(float*, const float*, float, float, int64_t, hipStream_t);
 void launch_prox_sgd(float*, const void*, int, const float*, float*, unsigned short*, float,
@@ -30,11 +32,8 @@ void launch_weighted_sum_rows(const float*, const float*, float*, int, int64_t, 
 void launch_bn_fwd(const void*, void*, float*, float*, float*, const float*, const float*, float*,
                    float*, int64_t*, float, float, int64_t, int, int, int, int, const void*,
                    hipStream_t);
-void launch_conv3x3_fwd_kb32(const void*, const void*, const float*, void*, int, int, int, int,
-                             int, hipStream_t);
+void launch_conv3x3(const ConvPlan*, const void*, const void*, const float*, void*, hipStream_t);
 void launch_pack_kb32(const void*, void*, int, int, int, hipStream_t);
-void launch_conv3x3_fwd_kzloop(const void*, const void*, const float*, void*, int, int, int, int,
-                               int, hipStream_t);
 void launch_conv3x3_wrw(const void*, const void*, void*, float*, void*, int, int, int, int, int,
                         hipStream_t);
 void launch_coo_count(const float*, float, int64_t, int64_t, int32_t*, hipStream_t);
@@ -47,8 +46,6 @@ void launch_in3d_fwd(const void*, void*, float*, float*, float*, const float*, c
 void launch_in3d_bwd(const void*, const void*, void*, float*, float*, float*, float*, float*,
                      const float*, const float*, const float*, const float*, int, int, int64_t,
                      int, float, hipStream_t);
-void launch_conv3x3_fwd(const void*, const void*, const float*, void*, int, int, int, int, int,
-                        hipStream_t);
 void launch_mkmmd_sums(const float*, const float*, double*, float*, int, int64_t, int64_t, int,
                        hipStream_t);
 void launch_mkmmd_backward(const float*, const float*, const float*, float*, int, int64_t,
@@ -258,7 +255,6 @@ int bn_dtype_of(const torch::Tensor& t) {
   return 0;
 }
 
-// x: NHWC-flattened [R, C] contiguous. Returns (y, save_mean, save_invstd).
 // wrw: dW for 3x3/s1/p1 NHWC bf16 (C,K in {64,128}; W=32 or 16 - the ResNet
 // layer-1/layer-2 families; >64-channel cases run as 64x64 sub-slices).
 // Returns bf16 [K, C, 3, 3] in channels_last memory (matches what
@@ -273,8 +269,9 @@ torch::Tensor conv3x3_wrw(torch::Tensor x, torch::Tensor dy) {
   TORCH_CHECK((W == 32 && H % 4 == 0) || (W == 16 && H % 8 == 0), "wrw supports W=32 (BH 4) or W=16 (BH 8)");
   auto bopts = torch::TensorOptions().dtype(torch::kBFloat16).device(x.device());
   // one 64x64 sub-slice at a time: partial/mid are reused across sub-launches
-  auto partial = torch::empty({256LL * 9 * 64 * 64}, bopts);
-  auto mid = torch::empty({16LL * 9 * 64 * 64},
+  const int64_t slice = 9LL * WRW_SLICE * WRW_SLICE;
+  auto partial = torch::empty({WRW_SPLITS * slice}, bopts);
+  auto mid = torch::empty({WRW_SG * slice},
                           torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
   auto dw = torch::empty_strided({K, C, 3, 3}, {(int64_t)9 * C, 1, (int64_t)3 * C, C}, bopts);
   launch_conv3x3_wrw(x.data_ptr(), dy.data_ptr(), partial.data_ptr(), mid.data_ptr<float>(),
@@ -282,6 +279,7 @@ torch::Tensor conv3x3_wrw(torch::Tensor x, torch::Tensor dy) {
   return dw;
 }
 
+// x: NHWC-flattened [R, C] contiguous. Returns (y, save_mean, save_invstd).
 std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, c10::optional<torch::Tensor> gamma,
                                         c10::optional<torch::Tensor> beta,
                                         c10::optional<torch::Tensor> running_mean,
@@ -345,62 +343,91 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy, torch::Tens
   return {dx, dgamma, dbeta};
 }
 
+ConvPlan conv_plan_checked_dims(ConvKernel kind, int64_t n, int64_t h, int64_t w, int64_t c,
+                                int64_t k) {
+  for (int64_t v : {n, h, w, c, k})
+    TORCH_CHECK(v >= 0 && v <= INT32_MAX, "conv3x3: dimension ", v, " out of range");
+  return conv_plan(kind, (int)n, (int)h, (int)w, (int)c, (int)k);
+}
+
+// Shared tail of the three forward bindings: validate tensors, take the
+// launch plan for (kind, shape), refuse a shape the kernel's LDS carve-up
+// cannot hold, launch from the plan. w is the kernel's weight layout, already
+// shape-checked by the caller; K its output channels.
+torch::Tensor conv3x3_run(ConvKernel kind, const torch::Tensor& x, const torch::Tensor& w,
+                          int64_t K, const c10::optional<torch::Tensor>& bias) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 4 && x.is_contiguous(),
+              "x must be NHWC bf16 contiguous on GPU");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous(),
+              "weights must be bf16 contiguous on GPU");
+  if (bias.has_value()) {
+    check_f32(*bias, "bias");
+    TORCH_CHECK(bias->numel() == K, "bias must be [K]");
+  }
+  ConvPlan p = conv_plan_checked_dims(kind, x.size(0), x.size(1), x.size(2), x.size(3), K);
+  TORCH_CHECK(p.fits, "conv3x3 ", conv_kernel_name(p.kernel), " cannot run N", p.N, " ", p.H, "x",
+              p.W, " C", p.C, "->K", p.K, ": ", p.reason);
+  auto y = torch::empty({p.N, p.H, p.W, p.K}, x.options());
+  launch_conv3x3(&p, x.data_ptr(), w.data_ptr(),
+                 bias.has_value() ? bias->data_ptr<float>() : nullptr, y.data_ptr(), stream());
+  return y;
+}
+
+// wimg must be the [K/32, C/64, 9, 32, 64] LDS image of x's channels; returns K.
+int64_t check_wimg(const torch::Tensor& x, const torch::Tensor& wimg) {
+  TORCH_CHECK(x.dim() == 4 && wimg.dim() == 5 && wimg.size(1) * 64 == x.size(3) &&
+              wimg.size(2) == 9 && wimg.size(3) == 32 && wimg.size(4) == 64,
+              "wimg must be [K/32, C/64, 9, 32, 64]");
+  return wimg.size(0) * 32;
+}
+
 // Direct 3x3 s1 p1 NHWC bf16 conv forward on MFMA (round-2 conv prototype).
 // x: [N, H, W, C] bf16 (channels-last); w: [9, C, K] bf16 prepacked
 // (torch weight [K, C, 3, 3] -> permute(2, 3, 1, 0).reshape(9, C, K));
 // returns [N, H, W, K] bf16.
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w,
                           c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 4 && x.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 3 && w.is_contiguous());
-  TORCH_CHECK(w.size(0) == 9 && w.size(1) == x.size(3), "w must be [9, C, K]");
-  int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), K = w.size(2);
-  TORCH_CHECK(W <= 32, "conv3x3_fwd prototype supports W <= 32");
-  if (bias.has_value()) check_f32(*bias, "bias");
-  auto y = torch::empty({N, H, W, K}, x.options());
-  launch_conv3x3_fwd(x.data_ptr(), w.data_ptr(),
-                     bias.has_value() ? bias->data_ptr<float>() : nullptr, y.data_ptr(),
-                     (int)N, (int)H, (int)W, (int)C, (int)K, stream());
-  return y;
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == 9 && x.dim() == 4 && w.size(1) == x.size(3),
+              "w must be [9, C, K]");
+  return conv3x3_run(CONV_FWD, x, w, w.size(2), bias);
 }
 
 // Variant C of the direct conv: KB = 32, both operands glds-pipelined.
-// wimg: [K/32, C/64, 9, 32, 64] bf16 — the exact LDS image, packed host-side
-// (ops/conv.py pack_weight_kb32). Requires C % 64 == 0 and K % 32 == 0.
+// wimg: [K/32, C/64, 9, 32, 64] bf16 — the exact LDS image (pack_kb32, or
+// ops/conv.py _image_kb32). Requires C % 64 == 0 and K % 32 == 0.
 torch::Tensor conv3x3_fwd_kb32(torch::Tensor x, torch::Tensor wimg,
                                c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 4 && x.is_contiguous());
-  TORCH_CHECK(wimg.is_cuda() && wimg.scalar_type() == torch::kBFloat16 && wimg.dim() == 5 &&
-              wimg.is_contiguous());
-  int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  int64_t K = wimg.size(0) * 32;
-  TORCH_CHECK(wimg.size(1) * 64 == C && wimg.size(2) == 9 && wimg.size(3) == 32 &&
-              wimg.size(4) == 64, "wimg must be [K/32, C/64, 9, 32, 64]");
-  TORCH_CHECK(W <= 32, "conv3x3 prototype supports W <= 32");
-  if (bias.has_value()) check_f32(*bias, "bias");
-  auto y = torch::empty({N, H, W, K}, x.options());
-  launch_conv3x3_fwd_kb32(x.data_ptr(), wimg.data_ptr(),
-                          bias.has_value() ? bias->data_ptr<float>() : nullptr, y.data_ptr(),
-                          (int)N, (int)H, (int)W, (int)C, (int)K, stream());
-  return y;
+  return conv3x3_run(CONV_KB32, x, wimg, check_wimg(x, wimg), bias);
 }
 
 // Variant D: input-resident multi-kz (one block per tile loops every
 // K-block; input staged once, weights pipelined). Same wimg pack as kb32.
 torch::Tensor conv3x3_fwd_kzloop(torch::Tensor x, torch::Tensor wimg,
                                  c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 4 && x.is_contiguous());
-  TORCH_CHECK(wimg.is_cuda() && wimg.scalar_type() == torch::kBFloat16 && wimg.dim() == 5 &&
-              wimg.is_contiguous());
-  int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  int64_t K = wimg.size(0) * 32;
-  TORCH_CHECK(wimg.size(1) * 64 == C && wimg.size(2) == 9, "wimg must be [K/32, C/64, 9, 32, 64]");
-  if (bias.has_value()) check_f32(*bias, "bias");
-  auto y = torch::empty({N, H, W, K}, x.options());
-  launch_conv3x3_fwd_kzloop(x.data_ptr(), wimg.data_ptr(),
-                            bias.has_value() ? bias->data_ptr<float>() : nullptr, y.data_ptr(),
-                            (int)N, (int)H, (int)W, (int)C, (int)K, stream());
-  return y;
+  return conv3x3_run(CONV_KZLOOP, x, wimg, check_wimg(x, wimg), bias);
+}
+
+// The launch plan conv3x3_fwd* would use for a shape, without launching:
+// kernel is "fwd" (what conv3x3_fwd picks), "base", "glds4", "glds8", "kb32"
+// or "kzloop". Callers gate on ["fits"]; needs no GPU.
+py::dict conv3x3_plan(const std::string& kernel, int64_t n, int64_t h, int64_t w, int64_t c,
+                      int64_t k) {
+  ConvKernel kind;
+  TORCH_CHECK(conv_kernel_from_name(kernel.c_str(), &kind), "unknown conv kernel '", kernel, "'");
+  ConvPlan p = conv_plan_checked_dims(kind, n, h, w, c, k);
+  py::dict d;
+  d["kernel"] = conv_kernel_name(p.kernel);
+  d["BH"] = p.BH;
+  d["SB"] = p.SB;
+  d["h_groups"] = p.h_groups;
+  d["n_tiles"] = p.n_tiles;
+  d["waves"] = p.waves;
+  d["m_rows"] = p.m_rows;
+  d["grid"] = py::make_tuple(p.grid_x, 1, p.grid_z);
+  d["in_chunks"] = p.in_chunks;
+  d["fits"] = p.fits;
+  d["reason"] = p.reason;
+  return d;
 }
 
 // Fused weight pack for conv3x3_fwd_kb32: [K, C, 3, 3] -> swizzled LDS-image
@@ -584,6 +611,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_fwd_kb32", &conv3x3_fwd_kb32,
         "direct 3x3 NHWC bf16 conv forward, KB=32 glds-pipelined variant");
   m.def("pack_kb32", &pack_kb32, "fused weight pack for conv3x3_fwd_kb32");
+  m.def("conv3x3_plan", &conv3x3_plan,
+        "launch plan (geometry, grid, fits/reason) of a conv3x3_fwd* kernel for a shape",
+        py::arg("kernel"), py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c"), py::arg("k"));
   m.def("conv3x3_fwd_kzloop", &conv3x3_fwd_kzloop,
         "direct 3x3 conv, input-resident multi-kz variant (KB=32)");
   m.def("coo_compact", &coo_compact,

@@ -22,11 +22,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
-#include <cstdlib>
+
+#include "conv_plan.h"  // LDS capacities + the checked launch geometry
 
 using bf16 = __bf16;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+// LDS-qualified operand pointers for conv_mma_taps. The helper is optimized on
+// its own before it is inlined; with generic pointers its unrolled address
+// math is formed in 64-bit flat form and costs ~30 extra VALU ops per c-chunk
+// and 12-36 VGPRs after inlining (kb32 measured 2% slower). Keep these typed.
+typedef const __attribute__((address_space(3))) __bf16* lds_bf16_ptr;
+typedef const __attribute__((address_space(3))) bf16x8* lds_bf16x8_ptr;
 
 // LDS bank-conflict swizzle (guide st_16x32): the halo/weight images are
 // 128-B rows (64 bf16 channels); a ds_read_b128 whose 16 lanes stride rows
@@ -37,16 +44,105 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // lane-linear and cannot be swizzled — guide rule 21).
 __device__ inline int conv_swz(int row) { return ((row >> 2) & 1) << 4; }
 
-#define CONV_KB 64      // output channels per block
-#define CONV_CB 64      // reduction channels per LDS stage
-#define CONV_THREADS 256
-
 // LDS: input halo tiles [SB][(BH+2)][(W+2)][CB] + weights [9][KB][CB] (both
-// bf16). Tile extent is SB*(BH+2)*(W+2) <= 304 positions across supported
-// shapes (W=32: 6*34=204; W=4, SB=8: 8*6*6=288).
-#define CONV_TILE_POS 304
-// one static LDS object (≈112 KB of the 160 KB/CU; single workgroup per CU)
+// bf16). conv_plan admits only tiles of SB*(BH+2)*(W+2) <= CONV_TILE_POS
+// positions. One static LDS object (≈112 KB of the 160 KB/CU; single
+// workgroup per CU).
 __shared__ __bf16 s_conv[CONV_TILE_POS * CONV_CB + 9 * CONV_CB * CONV_KB];
+
+// ---------------------------------------------------------------------------
+// Pieces shared by the four forward kernels. Each kernel keeps its own
+// staging, double-buffering and barriers; the tile decode, the MFMA tap loop
+// and the epilogue exist once.
+// ---------------------------------------------------------------------------
+struct conv_tile {
+  int H, W;
+  int n0, h0;   // first sample / first image row of the tile
+  int sb, bh;   // samples / rows actually present (ragged last tile)
+  int pps;      // positions per sample-section = bh * W
+  int m_count;  // valid output positions = sb * pps
+
+  __device__ __forceinline__ static conv_tile decode(int tile, int Nn, int H, int W, int BH,
+                                                     int SB, int h_groups) {
+    conv_tile t;
+    t.H = H;
+    t.W = W;
+    int hg = tile % h_groups;
+    t.n0 = (tile / h_groups) * SB;
+    t.sb = min(SB, Nn - t.n0);
+    t.h0 = hg * BH;
+    t.bh = min(BH, H - t.h0);
+    t.pps = t.bh * W;
+    t.m_count = t.sb * t.pps;
+    return t;
+  }
+};
+
+// 9 taps x (CB/32) mfma-K steps over one staged c-chunk. The wave owns tile
+// rows wave_m*32 .. +31 (two 16-row A fragments) and QS 16-wide output-channel
+// slots starting at slot qbase; s_w is [9][kb_rows][CB].
+template <int QS>
+__device__ __forceinline__ void conv_mma_taps(lds_bf16_ptr s_in, lds_bf16_ptr s_w,
+                                              int kb_rows, int wave_m, int qbase, int lane,
+                                              const conv_tile& tl, f32x4 (&acc)[2][QS]) {
+  int tile_w = tl.W + 2;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    int dy = tap / 3, dx = tap % 3;
+#pragma unroll
+    for (int ck = 0; ck < CONV_CB / 32; ++ck) {
+      int kbase = ck * 32 + (lane >> 4) * 8;
+      bf16x8 afrag[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        int m = wave_m * 32 + t * 16 + (lane & 15);
+        int s = m / tl.pps, rem = m % tl.pps;
+        int hh = rem / tl.W, ww = rem % tl.W;
+        int apos = (s * (tl.bh + 2) + hh + dy) * tile_w + (ww + dx);
+        // channel-contiguous: one 16-byte LDS read per fragment
+        bf16x8 a = *(lds_bf16x8_ptr)&s_in[apos * CONV_CB + (kbase ^ conv_swz(apos))];
+        if (m >= tl.m_count) a = bf16x8{};
+        afrag[t] = a;
+      }
+#pragma unroll
+      for (int q = 0; q < QS; ++q) {
+        int br = tap * kb_rows + (qbase + q) * 16 + (lane & 15);
+        bf16x8 bfrag = *(lds_bf16x8_ptr)&s_w[br * CONV_CB + (kbase ^ conv_swz(br))];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[t], bfrag, acc[t][q], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// Epilogue: fp32 acc (+bias) -> bf16 NHWC, masked to the ragged tile and to K.
+// The bias of channel slot q is bias[bias_base + q * bias_qstride]: the global
+// [K] vector (base kb0 + qbase*16 + (lane&15), stride 16) or a per-lane
+// register cache (base 0, stride 1). nullptr = no bias.
+template <int QS>
+__device__ __forceinline__ void conv_store_tile(bf16* __restrict__ y, const float* bias,
+                                                int bias_base, int bias_qstride, int kb0, int K,
+                                                int wave_m, int qbase, int lane,
+                                                const conv_tile& tl, const f32x4 (&acc)[2][QS]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int q = 0; q < QS; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int m = wave_m * 32 + t * 16 + (lane >> 4) * 4 + r;
+        int k = (qbase + q) * 16 + (lane & 15);
+        if (m < tl.m_count && kb0 + k < K) {
+          int s = m / tl.pps, rem = m % tl.pps;
+          int hh = rem / tl.W, ww = rem % tl.W;
+          float v = acc[t][q][r];
+          if (bias != nullptr) v += bias[bias_base + q * bias_qstride];
+          y[(((int64_t)(tl.n0 + s) * tl.H + tl.h0 + hh) * tl.W + ww) * (int64_t)K + kb0 + k] =
+              (bf16)v;
+        }
+      }
+}
 
 __device__ inline void stage_weights(const bf16* __restrict__ w, __bf16* __restrict__ s_w,
                                      int C, int K, int c0, int cb, int kb0, int tid,
@@ -93,13 +189,8 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_fwd_kernel(
   }
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    int hg = tile % h_groups;
-    int n0 = (tile / h_groups) * SB;
-    int sb = min(SB, Nn - n0);
-    int h0 = hg * BH;
-    int bh = min(BH, H - h0);
-    int pps = bh * W;             // positions per sample-section
-    int m_count = sb * pps;
+    const conv_tile tl = conv_tile::decode(tile, Nn, H, W, BH, SB, h_groups);
+    const int n0 = tl.n0, h0 = tl.h0, sb = tl.sb, bh = tl.bh;
 
     f32x4 acc[2][4];
 #pragma unroll
@@ -131,59 +222,13 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_fwd_kernel(
       if (!persistent_w) stage_weights(w, s_w, C, K, c0, cb, kb0, tid);
       __syncthreads();
 
-      // ---- 9 taps x (CB/32) mfma-K steps ----
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        int dy = tap / 3, dx = tap % 3;
-#pragma unroll
-        for (int ck = 0; ck < CONV_CB / 32; ++ck) {
-          int kbase = ck * 32 + (lane >> 4) * 8;
-          bf16x8 afrag[2];
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            int m = wave * 32 + t * 16 + (lane & 15);
-            int s = m / pps, rem = m % pps;
-            int hh = rem / W, ww = rem % W;
-            int apos = (s * (bh + 2) + hh + dy) * tile_w + (ww + dx);
-            // channel-contiguous: one 16-byte LDS read per fragment
-            bf16x8 a = *reinterpret_cast<const bf16x8*>(
-                &s_in[apos * CONV_CB + (kbase ^ conv_swz(apos))]);
-            if (m >= m_count) a = bf16x8{};
-            afrag[t] = a;
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            int br = tap * CONV_KB + q * 16 + (lane & 15);
-            bf16x8 bfrag =
-                *reinterpret_cast<const bf16x8*>(&s_w[br * CONV_CB + (kbase ^ conv_swz(br))]);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-              acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[t], bfrag, acc[t][q], 0, 0, 0);
-          }
-        }
-      }
+      conv_mma_taps<4>((lds_bf16_ptr)s_in, (lds_bf16_ptr)s_w, CONV_KB, wave, 0, lane, tl, acc);
       // covers both the next c-chunk's s_in overwrite and, on the last
       // chunk, the next TILE's s_in overwrite (epilogue touches no LDS)
       __syncthreads();
     }
 
-    // ---- epilogue: fp32 acc (+bias) -> bf16 NHWC ----
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int m = wave * 32 + t * 16 + (lane >> 4) * 4 + r;
-          int k = q * 16 + (lane & 15);
-          if (m < m_count && kb0 + k < K) {
-            int s = m / pps, rem = m % pps;
-            int hh = rem / W, ww = rem % W;
-            float v = acc[t][q][r];
-            if (bias != nullptr) v += bias[kb0 + k];
-            y[(((int64_t)(n0 + s) * H + h0 + hh) * W + ww) * (int64_t)K + kb0 + k] = (bf16)v;
-          }
-        }
+    conv_store_tile<4>(y, bias, kb0 + (lane & 15), 16, kb0, K, wave, 0, lane, tl, acc);
   }
 }
 
@@ -201,17 +246,18 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_fwd_kernel(
 // the LDS destination of glds is wave-uniform base + lane*16 and cannot be
 // masked per-lane.
 // ---------------------------------------------------------------------------
-#define CONV_GLDS_CHUNK_CAP 1792   // 4-wave variant: 16 B chunks/buffer (32x32 M=128: 1632)
-#define CONV_GLDS_CHUNK_CAP8 2752  // 8-wave variant (32x32 M=256: 10*34*8 = 2720)
-// NOTE both caps are gated on round_up(chunks, 64): glds bases are 64-lane
-// aligned, so the ragged last group writes up to round_up(chunks, 64) - 1;
-// an exact-sized buffer lets it spill into the neighbouring buffer / the
-// persistent weights (the round-1 8-wave corruption bug).
+// NOTE every glds buffer cap (conv_plan.h) is gated on round_up(chunks, 64):
+// glds bases are 64-lane aligned, so the ragged last group writes up to
+// round_up(chunks, 64) - 1; an exact-sized buffer lets it spill into the
+// neighbouring buffer / the persistent weights (the round-1 8-wave
+// corruption bug).
 __device__ __align__(16) __bf16 conv_zero16[8] = {};
 
 __device__ inline void issue_glds_input(const bf16* __restrict__ x, __bf16* __restrict__ dst,
-                                        int n0, int h0, int sb, int bh, int H, int W, int C,
-                                        int c0, int tile_w, int tid, int nthreads) {
+                                        const conv_tile& tl, int C, int c0, int tid,
+                                        int nthreads) {
+  const int n0 = tl.n0, h0 = tl.h0, sb = tl.sb, bh = tl.bh, H = tl.H, W = tl.W;
+  int tile_w = W + 2;
   int wave = tid >> 6, lane = tid & 63;
   int cpv = CONV_CB / 8;  // LDS image stride is CONV_CB channels per position
   int total_chunks = sb * (bh + 2) * tile_w * cpv;
@@ -247,47 +293,30 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3_fwd_glds_kernel(
   __shared__ __bf16 s_mem[2 * CAP * 8 + 9 * CONV_CB * CONV_KB];
   __bf16* s_w = s_mem + 2 * CAP * 8;
   int kb0 = blockIdx.z * CONV_KB;
-  int tile_w = W + 2;
   int tid = threadIdx.x;
   int wave = tid >> 6, lane = tid & 63;
 
   stage_weights(w, s_w, C, K, 0, C, kb0, tid, NT);  // persistent: staged ONCE
-  float breg[4];
+  float breg[4];  // this lane's four bias values, loaded once for all tiles
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     int k = kb0 + q * 16 + (lane & 15);
     breg[q] = (bias != nullptr && k < K) ? bias[k] : 0.0f;
   }
 
-  auto tile_geom = [&](int tile, int& n0, int& h0, int& sb, int& bh) {
-    int hg = tile % h_groups;
-    n0 = (tile / h_groups) * SB;
-    sb = min(SB, Nn - n0);
-    h0 = hg * BH;
-    bh = min(BH, H - h0);
-  };
-
   int tile = blockIdx.x;
-  if (tile < n_tiles) {
-    int n0, h0, sb, bh;
-    tile_geom(tile, n0, h0, sb, bh);
-    issue_glds_input(x, s_mem, n0, h0, sb, bh, H, W, C, 0, tile_w, tid, NT);
-  }
+  if (tile < n_tiles)
+    issue_glds_input(x, s_mem, conv_tile::decode(tile, Nn, H, W, BH, SB, h_groups), C, 0, tid,
+                     NT);
   __syncthreads();  // drains prologue glds (vmcnt 0) + weight ds_writes
   int cur = 0;
 
   for (; tile < n_tiles; tile += gridDim.x) {
-    int n0, h0, sb, bh;
-    tile_geom(tile, n0, h0, sb, bh);
-    int pps = bh * W;
-    int m_count = sb * pps;
+    const conv_tile tl = conv_tile::decode(tile, Nn, H, W, BH, SB, h_groups);
     int nxt = tile + gridDim.x;
-    if (nxt < n_tiles) {
-      int nn0, nh0, nsb, nbh;
-      tile_geom(nxt, nn0, nh0, nsb, nbh);
-      issue_glds_input(x, s_mem + (1 - cur) * (CAP * 8), nn0, nh0, nsb, nbh, H, W, C, 0,
-                       tile_w, tid, NT);
-    }
+    if (nxt < n_tiles)
+      issue_glds_input(x, s_mem + (1 - cur) * (CAP * 8),
+                       conv_tile::decode(nxt, Nn, H, W, BH, SB, h_groups), C, 0, tid, NT);
     const __bf16* s_in = s_mem + cur * (CAP * 8);
 
     f32x4 acc[2][4];
@@ -295,52 +324,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3_fwd_glds_kernel(
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      int dy = tap / 3, dx = tap % 3;
-#pragma unroll
-      for (int ck = 0; ck < CONV_CB / 32; ++ck) {
-        int kbase = ck * 32 + (lane >> 4) * 8;
-        bf16x8 afrag[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          int m = wave * 32 + t * 16 + (lane & 15);
-          int sidx = m / pps, rem = m % pps;
-          int hh = rem / W, ww = rem % W;
-          int apos = (sidx * (bh + 2) + hh + dy) * tile_w + (ww + dx);
-          bf16x8 a = *reinterpret_cast<const bf16x8*>(
-              &s_in[apos * CONV_CB + (kbase ^ conv_swz(apos))]);
-          if (m >= m_count) a = bf16x8{};
-          afrag[t] = a;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          int br = tap * CONV_KB + q * 16 + (lane & 15);
-          bf16x8 bfrag =
-              *reinterpret_cast<const bf16x8*>(&s_w[br * CONV_CB + (kbase ^ conv_swz(br))]);
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[t], bfrag, acc[t][q], 0, 0, 0);
-        }
-      }
-    }
-
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int m = wave * 32 + t * 16 + (lane >> 4) * 4 + r;
-          int k = q * 16 + (lane & 15);
-          if (m < m_count && kb0 + k < K) {
-            int sidx = m / pps, rem = m % pps;
-            int hh = rem / W, ww = rem % W;
-            y[(((int64_t)(n0 + sidx) * H + h0 + hh) * W + ww) * (int64_t)K + kb0 + k] =
-                (bf16)(acc[t][q][r] + breg[q]);
-          }
-        }
+    conv_mma_taps<4>((lds_bf16_ptr)s_in, (lds_bf16_ptr)s_w, CONV_KB, wave, 0, lane, tl, acc);
+    conv_store_tile<4>(y, breg, 0, 1, kb0, K, wave, 0, lane, tl, acc);
     __syncthreads();  // all waves done reading s_in; prefetch glds drained
     cur ^= 1;
   }
@@ -355,9 +340,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3_fwd_glds_kernel(
 // round-1 kernel filled only 128 of 256 CUs; KB = 32 doubles kz and fills the
 // chip without split-C partials).
 // ---------------------------------------------------------------------------
-#define CONVC_KB 32
-#define CONVC_CHUNK_CAP 2304  // max input chunks (4x4 SB=8: 288 pos * 8)
-#define CONVC_WCHUNKS (9 * CONVC_KB * CONV_CB / 8)  // 2304 weight chunks/slab
 __shared__ __bf16 s_convc[2 * CONVC_CHUNK_CAP * 8 + 2 * CONVC_WCHUNKS * 8];
 
 __device__ inline void issue_glds_slab(const bf16* __restrict__ src_base, __bf16* __restrict__ dst,
@@ -380,21 +362,13 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_fwd_kb32_kernel(
   int tile = blockIdx.x;
   int kzi = blockIdx.z;
   int kb0 = kzi * CONVC_KB;
-  int tile_w = W + 2;
   int tid = threadIdx.x;
   int wave = tid >> 6, lane = tid & 63;
   int n_cchunks = (C + CONV_CB - 1) / CONV_CB;
-
-  int hg = tile % h_groups;
-  int n0 = (tile / h_groups) * SB;
-  int sb = min(SB, Nn - n0);
-  int h0 = hg * BH;
-  int bh = min(BH, H - h0);
-  int pps = bh * W;
-  int m_count = sb * pps;
+  const conv_tile tl = conv_tile::decode(tile, Nn, H, W, BH, SB, h_groups);
 
   const bf16* wslab0 = wimg + ((size_t)kzi * n_cchunks) * (CONVC_WCHUNKS * 8);
-  issue_glds_input(x, s_convc, n0, h0, sb, bh, H, W, C, 0, tile_w, tid, CONV_THREADS);
+  issue_glds_input(x, s_convc, tl, C, 0, tid, CONV_THREADS);
   issue_glds_slab(wslab0, s_convc + 2 * CONVC_CHUNK_CAP * 8, CONVC_WCHUNKS, tid);
   __syncthreads();
 
@@ -407,128 +381,20 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_fwd_kb32_kernel(
   int cur = 0;
   for (int ci = 0; ci < n_cchunks; ++ci) {
     if (ci + 1 < n_cchunks) {
-      issue_glds_input(x, s_convc + (1 - cur) * (CONVC_CHUNK_CAP * 8), n0, h0, sb, bh, H, W, C,
-                       (ci + 1) * CONV_CB, tile_w, tid, CONV_THREADS);
+      issue_glds_input(x, s_convc + (1 - cur) * (CONVC_CHUNK_CAP * 8), tl, C,
+                       (ci + 1) * CONV_CB, tid, CONV_THREADS);
       issue_glds_slab(wslab0 + (size_t)(ci + 1) * (CONVC_WCHUNKS * 8),
                       s_convc + 2 * CONVC_CHUNK_CAP * 8 + (1 - cur) * (CONVC_WCHUNKS * 8),
                       CONVC_WCHUNKS, tid);
     }
     const __bf16* sin = s_convc + cur * (CONVC_CHUNK_CAP * 8);
     const __bf16* sw = s_convc + 2 * CONVC_CHUNK_CAP * 8 + cur * (CONVC_WCHUNKS * 8);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      int dy = tap / 3, dx = tap % 3;
-#pragma unroll
-      for (int ck = 0; ck < CONV_CB / 32; ++ck) {
-        int kbase = ck * 32 + (lane >> 4) * 8;
-        bf16x8 afrag[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          int m = wave * 32 + t * 16 + (lane & 15);
-          int sidx = m / pps, rem = m % pps;
-          int hh = rem / W, ww = rem % W;
-          int apos = (sidx * (bh + 2) + hh + dy) * tile_w + (ww + dx);
-          bf16x8 a = *reinterpret_cast<const bf16x8*>(
-              &sin[apos * CONV_CB + (kbase ^ conv_swz(apos))]);
-          if (m >= m_count) a = bf16x8{};
-          afrag[t] = a;
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          int br = tap * CONVC_KB + q * 16 + (lane & 15);
-          bf16x8 bfrag =
-              *reinterpret_cast<const bf16x8*>(&sw[br * CONV_CB + (kbase ^ conv_swz(br))]);
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[t], bfrag, acc[t][q], 0, 0, 0);
-        }
-      }
-    }
+    conv_mma_taps<2>((lds_bf16_ptr)sin, (lds_bf16_ptr)sw, CONVC_KB, wave, 0, lane, tl, acc);
     __syncthreads();  // drains next chunk's DMA; all waves done with cur
     cur ^= 1;
   }
 
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int m = wave * 32 + t * 16 + (lane >> 4) * 4 + r;
-        int k = q * 16 + (lane & 15);
-        if (m < m_count && kb0 + k < K) {
-          int sidx = m / pps, rem = m % pps;
-          int hh = rem / W, ww = rem % W;
-          float v = acc[t][q][r];
-          if (bias != nullptr) v += bias[kb0 + k];
-          y[(((int64_t)(n0 + sidx) * H + h0 + hh) * W + ww) * (int64_t)K + kb0 + k] = (bf16)v;
-        }
-      }
-}
-
-static inline void conv_tile_geom(int Nn, int H, int W, int M, int& BH, int& SB, int& h_groups,
-                                  int& n_tiles) {
-  BH = std::min(std::max(M / W, 1), H);
-  SB = std::max(M / (H * W), 1);  // pack small images, several per block
-  SB = std::min(SB, Nn);
-  h_groups = (H + BH - 1) / BH;
-  n_tiles = ((Nn + SB - 1) / SB) * h_groups;
-}
-
-extern "C" void launch_conv3x3_fwd(const void* x, const void* w, const float* bias, void* y,
-                                   int Nn, int H, int W, int C, int K, hipStream_t s) {
-  int kz = (K + CONV_KB - 1) / CONV_KB;
-  static int cap = [] {
-    const char* e = getenv("FL4_CONVB_GRID");
-    return e ? atoi(e) : 256;
-  }();
-  static int force_waves = [] {
-    const char* e = getenv("FL4_CONVB_WAVES");
-    return e ? atoi(e) : -1;  // -1 auto, 0 disable variant B, 4/8 force
-  }();
-  if (C <= CONV_CB && C % 8 == 0 && force_waves != 0) {
-    // Variant B: persistent weights + pipelined input DMA. Prefer the 8-wave
-    // (M = 256) instantiation — 2 waves/SIMD hides ds_read/MFMA latency at
-    // 1 block/CU — then the 4-wave one; fall through if the halo won't fit.
-    int BH, SB, h_groups, n_tiles;
-    conv_tile_geom(Nn, H, W, 256, BH, SB, h_groups, n_tiles);
-    int chunks8 = SB * (BH + 2) * (W + 2) * (CONV_CB / 8);
-    if (((chunks8 + 63) & ~63) <= CONV_GLDS_CHUNK_CAP8 && force_waves != 4) {
-      dim3 grid(std::min(n_tiles, cap), 1, kz);
-      conv3x3_fwd_glds_kernel<8><<<grid, 512, 0, s>>>(
-          (const bf16*)x, (const bf16*)w, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles,
-          h_groups);
-      return;
-    }
-    conv_tile_geom(Nn, H, W, 128, BH, SB, h_groups, n_tiles);
-    int chunks4 = SB * (BH + 2) * (W + 2) * (CONV_CB / 8);
-    if (((chunks4 + 63) & ~63) <= CONV_GLDS_CHUNK_CAP) {
-      dim3 grid(std::min(n_tiles, 2 * cap), 1, kz);
-      conv3x3_fwd_glds_kernel<4><<<grid, CONV_THREADS, 0, s>>>(
-          (const bf16*)x, (const bf16*)w, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles,
-          h_groups);
-      return;
-    }
-  }
-  int BH, SB, h_groups, n_tiles;
-  conv_tile_geom(Nn, H, W, 128, BH, SB, h_groups, n_tiles);
-  dim3 grid(n_tiles, 1, kz);
-  conv3x3_fwd_kernel<<<grid, CONV_THREADS, 0, s>>>(
-      (const bf16*)x, (const bf16*)w, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles, h_groups);
-}
-
-// Variant C entry: caller supplies the LDS-image weight pack (see
-// ops/conv.py pack_weight_kb32). Requires C % 64 == 0, K % 32 == 0.
-extern "C" void launch_conv3x3_fwd_kb32(const void* x, const void* wimg, const float* bias,
-                                        void* y, int Nn, int H, int W, int C, int K,
-                                        hipStream_t s) {
-  int BH, SB, h_groups, n_tiles;
-  conv_tile_geom(Nn, H, W, 128, BH, SB, h_groups, n_tiles);
-  int kz = K / CONVC_KB;
-  dim3 grid(n_tiles, 1, kz);
-  conv3x3_fwd_kb32_kernel<<<grid, CONV_THREADS, 0, s>>>(
-      (const bf16*)x, (const bf16*)wimg, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles,
-      h_groups);
+  conv_store_tile<2>(y, bias, kb0 + (lane & 15), 16, kb0, K, wave, 0, lane, tl, acc);
 }
 
 // ---------------------------------------------------------------------------
@@ -584,52 +450,40 @@ extern "C" void launch_pack_kb32(const void* w, void* out, int K, int C, int mod
 // restaging per kz (variant C re-reads input KZ times), prologue amortized
 // over KZ*CC chunks.
 // ---------------------------------------------------------------------------
-#define CONVD_IN_CAP 1664      // 16-B chunks per input c-chunk (16x16: 1440, 8x8 SB2: 1600) + ragged-glds slack
-#define CONVD_MAX_CC 2         // resident input c-chunks
 __shared__ __bf16 s_convd[CONVD_MAX_CC * CONVD_IN_CAP * 8 + 2 * CONVC_WCHUNKS * 8];
+constexpr int CONVD_THREADS = 512;
 
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void conv3x3_fwd_kzloop_kernel(
+__global__ __launch_bounds__(CONVD_THREADS) void conv3x3_fwd_kzloop_kernel(
     const bf16* __restrict__ x,
     const bf16* __restrict__ wimg,  // [K/32][C/64][9][32][64] contiguous slabs
     const float* __restrict__ bias, bf16* __restrict__ y, int Nn, int H, int W, int C, int K,
     int BH, int SB, int n_tiles, int h_groups) {
-  // WAVES == 4: each wave owns a 32(M) x 32(K) tile (acc[2][2]).
-  // WAVES == 8: wave pairs split the K dim — wave (w&3) covers M rows, bit
-  // w>>2 selects which 16-wide K half it computes (acc[2][1]) => 2 waves per
-  // SIMD for ds_read/MFMA latency hiding at the same LDS footprint.
-  constexpr int NT = WAVES * 64;
-  constexpr int QS = (WAVES == 8) ? 1 : 2;  // q slots per wave
+  // 8 waves; wave pairs split the K dim — wave (w&3) covers M rows, bit w>>2
+  // selects which 16-wide K half it computes (acc[2][1]) => 2 waves per SIMD
+  // for ds_read/MFMA latency hiding. (A 4-wave acc[2][2] form lost its A/B
+  // on every shape measured: profiles/kernels_summary.md.)
   int tile = blockIdx.x;
-  int tile_w = W + 2;
   int tid = threadIdx.x;
   int wave = tid >> 6, lane = tid & 63;
-  int wave_m = (WAVES == 8) ? (wave & 3) : wave;
-  int qbase = (WAVES == 8) ? (wave >> 2) : 0;
+  int wave_m = wave & 3;
+  int qbase = wave >> 2;
   int n_cchunks = (C + CONV_CB - 1) / CONV_CB;
   int kz = K / CONVC_KB;
-
-  int hg = tile % h_groups;
-  int n0 = (tile / h_groups) * SB;
-  int sb = min(SB, Nn - n0);
-  int h0 = hg * BH;
-  int bh = min(BH, H - h0);
-  int pps = bh * W;
-  int m_count = sb * pps;
+  const conv_tile tl = conv_tile::decode(tile, Nn, H, W, BH, SB, h_groups);
 
   __bf16* s_w0 = s_convd + CONVD_MAX_CC * CONVD_IN_CAP * 8;
   // stage ALL input c-chunks once + the first weight slab
   for (int ci = 0; ci < n_cchunks; ++ci)
-    issue_glds_input(x, s_convd + (size_t)ci * (CONVD_IN_CAP * 8), n0, h0, sb, bh, H, W, C,
-                     ci * CONV_CB, tile_w, tid, NT);
+    issue_glds_input(x, s_convd + (size_t)ci * (CONVD_IN_CAP * 8), tl, C, ci * CONV_CB, tid,
+                     CONVD_THREADS);
   issue_glds_slab(wimg, s_w0, CONVC_WCHUNKS, tid);
   __syncthreads();
 
-  f32x4 acc[2][QS];
+  f32x4 acc[2][1];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int q = 0; q < QS; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 1; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   int total = kz * n_cchunks;
   int cur = 0;
@@ -641,80 +495,35 @@ __global__ __launch_bounds__(WAVES * 64) void conv3x3_fwd_kzloop_kernel(
                       s_w0 + (size_t)(1 - cur) * (CONVC_WCHUNKS * 8), CONVC_WCHUNKS, tid);
     const __bf16* sin = s_convd + (size_t)ci * (CONVD_IN_CAP * 8);
     const __bf16* sw = s_w0 + (size_t)cur * (CONVC_WCHUNKS * 8);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      int dy = tap / 3, dx = tap % 3;
-#pragma unroll
-      for (int ck = 0; ck < CONV_CB / 32; ++ck) {
-        int kbase = ck * 32 + (lane >> 4) * 8;
-        bf16x8 afrag[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          int m = wave_m * 32 + t * 16 + (lane & 15);
-          int sidx = m / pps, rem = m % pps;
-          int hh = rem / W, ww = rem % W;
-          int apos = (sidx * (bh + 2) + hh + dy) * tile_w + (ww + dx);
-          bf16x8 a = *reinterpret_cast<const bf16x8*>(
-              &sin[apos * CONV_CB + (kbase ^ conv_swz(apos))]);
-          if (m >= m_count) a = bf16x8{};
-          afrag[t] = a;
-        }
-#pragma unroll
-        for (int q = 0; q < QS; ++q) {
-          int br = tap * CONVC_KB + (qbase + q) * 16 + (lane & 15);
-          bf16x8 bfrag =
-              *reinterpret_cast<const bf16x8*>(&sw[br * CONV_CB + (kbase ^ conv_swz(br))]);
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag[t], bfrag, acc[t][q], 0, 0, 0);
-        }
-      }
-    }
+    conv_mma_taps<1>((lds_bf16_ptr)sin, (lds_bf16_ptr)sw, CONVC_KB, wave_m, qbase, lane, tl,
+                     acc);
     if (ci == n_cchunks - 1) {
       int kb0 = kzi * CONVC_KB;
+      conv_store_tile<1>(y, bias, kb0 + qbase * 16 + (lane & 15), 16, kb0, K, wave_m, qbase,
+                         lane, tl, acc);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int q = 0; q < QS; ++q) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            int m = wave_m * 32 + t * 16 + (lane >> 4) * 4 + r;
-            int k = (qbase + q) * 16 + (lane & 15);
-            if (m < m_count && kb0 + k < K) {
-              int sidx = m / pps, rem = m % pps;
-              int hh = rem / W, ww = rem % W;
-              float v = acc[t][q][r];
-              if (bias != nullptr) v += bias[kb0 + k];
-              y[(((int64_t)(n0 + sidx) * H + h0 + hh) * W + ww) * (int64_t)K + kb0 + k] = (bf16)v;
-            }
-          }
-          acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        for (int q = 0; q < 1; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     __syncthreads();
     cur ^= 1;
   }
 }
 
-extern "C" void launch_conv3x3_fwd_kzloop(const void* x, const void* wimg, const float* bias,
-                                          void* y, int Nn, int H, int W, int C, int K,
-                                          hipStream_t s) {
-  int BH, SB, h_groups, n_tiles;
-  conv_tile_geom(Nn, H, W, 128, BH, SB, h_groups, n_tiles);
-  dim3 grid(n_tiles, 1, 1);
-  static int waves = [] {
-    const char* e = getenv("FL4_KZLOOP_WAVES");
-    return e ? atoi(e) : 8;
-  }();
-  if (waves == 8) {
-    conv3x3_fwd_kzloop_kernel<8><<<grid, 512, 0, s>>>(
-        (const bf16*)x, (const bf16*)wimg, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles,
-        h_groups);
-  } else {
-    conv3x3_fwd_kzloop_kernel<4><<<grid, CONV_THREADS, 0, s>>>(
-        (const bf16*)x, (const bf16*)wimg, bias, (bf16*)y, Nn, H, W, C, K, BH, SB, n_tiles,
-        h_groups);
-  }
+// The one forward launcher: p is a conv_plan() result the caller has checked
+// (p.fits); geometry, block size and grid all come from it. w is [9, C, K]
+// for base/glds and the pack_kb32 LDS image for kb32/kzloop.
+extern "C" void launch_conv3x3(const ConvPlan* p, const void* x, const void* w,
+                               const float* bias, void* y, hipStream_t s) {
+  auto kernel = p->kernel == CONV_BASE    ? conv3x3_fwd_kernel
+                : p->kernel == CONV_GLDS4 ? conv3x3_fwd_glds_kernel<4>
+                : p->kernel == CONV_GLDS8 ? conv3x3_fwd_glds_kernel<8>
+                : p->kernel == CONV_KB32  ? conv3x3_fwd_kb32_kernel
+                                          : conv3x3_fwd_kzloop_kernel;
+  kernel<<<dim3(p->grid_x, 1, p->grid_z), p->waves * 64, 0, s>>>(
+      (const bf16*)x, (const bf16*)w, bias, (bf16*)y, p->N, p->H, p->W, p->C, p->K, p->BH, p->SB,
+      p->n_tiles, p->h_groups);
 }
 
 // ---------------------------------------------------------------------------
@@ -732,8 +541,9 @@ extern "C" void launch_conv3x3_fwd_kzloop(const void* x, const void* wimg, const
 // m-groups (c) x 2 n-groups (k); acc = 2 n-tiles x 9 taps x f32x4 per wave.
 // Each WG accumulates its tile range in registers and writes ONE fp32
 // partial dW; a combine kernel reduces the fixed split count (deterministic).
+// The split count WRW_SPLITS, the combine fan-out WRW_SG and the 64x64
+// slice size live in conv_plan.h (the binding sizes the workspaces from them).
 // ---------------------------------------------------------------------------
-#define WRW_SPLITS 256
 // x is staged THREE times, one copy per horizontal tap shift, so every
 // MFMA A-fragment read is a 16B-aligned ds_read_b128 (a single shifted copy
 // forces odd-u16 offsets -> scalar LDS reads, measured 0.46x MIOpen).
@@ -850,7 +660,6 @@ __global__ __launch_bounds__(512) void conv3x3_wrw_kernel(
 // strided splits left most of the chip idle (~25 us — dominated the call);
 // stage 1 fans the split dim across gridDim.y, stage 2 folds the remainder
 // and scatters the 64x64 slice into the full [K,C,3,3] channels_last dW.
-#define WRW_SG 16  // split groups in stage 1
 __global__ __launch_bounds__(256) void conv3x3_wrw_combine1_kernel(
     const bf16* __restrict__ partial, float* __restrict__ mid, int total, int splits) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -879,11 +688,11 @@ __global__ __launch_bounds__(256) void conv3x3_wrw_combine2_kernel(
 extern "C" void launch_conv3x3_wrw(const void* x, const void* dy, void* partial, float* mid,
                                    void* dw_cl, int Nn, int H, int W, int C, int K,
                                    hipStream_t s) {
-  const int total = 9 * 64 * 64;
+  const int total = 9 * WRW_SLICE * WRW_SLICE;
   dim3 g1((total + 255) / 256, WRW_SG, 1);
   dim3 g2((total + 255) / 256, 1, 1);
-  for (int c0 = 0; c0 < C; c0 += 64)
-    for (int k0 = 0; k0 < K; k0 += 64) {
+  for (int c0 = 0; c0 < C; c0 += WRW_SLICE)
+    for (int k0 = 0; k0 < K; k0 += WRW_SLICE) {
       if (W == 32) {
         int n_tiles = Nn * (H / 4);
         conv3x3_wrw_kernel<32, 4><<<dim3(WRW_SPLITS, 1, 1), 512, 0, s>>>(

@@ -674,6 +674,91 @@ def test_conv3x3_kzloop_matches_reference():
     assert x.grad is not None and m.weight.grad is not None
 
 
+# (kernel, (N, H, W, C, K), bias): every forward kernel on its ragged / capacity
+# / multi-chunk edges. The kernels sum in a fixed order, so the bf16 output
+# bytes are reproducible; tests/golden/conv3x3_fwd_digests.json holds their
+# sha256 as recorded before the kernels were refactored onto shared helpers.
+_CONV_DIGEST_CASES = [
+    ("base", (2, 6, 16, 96, 80), True),      # ragged C, K and h-group
+    ("base", (5, 4, 4, 128, 64), False),     # ragged sample pack, two c-chunks
+    ("glds8", (65, 32, 32, 64, 64), True),   # 260 tiles > 256-block grid: prefetch loop
+    ("glds8", (4, 16, 16, 24, 64), False),   # C < 64 zero-page lanes
+    ("glds4", (7, 8, 8, 64, 32), False),     # ragged last pack, K < 64
+    ("kb32", (8, 4, 4, 128, 64), False),     # 288 positions = capacity, double-buffered
+    ("kb32", (5, 4, 4, 64, 32), False),
+    ("kb32", (3, 8, 8, 128, 128), True),
+    ("kb32", (128, 4, 4, 512, 512), False),  # the flagship bench's shape: 8 c-chunks, 16 kz
+    ("kzloop", (3, 16, 16, 128, 64), False),
+    ("kzloop", (2, 16, 16, 64, 128), True),
+    ("kzloop", (3, 8, 8, 128, 64), False),
+]
+
+
+@requires_gpu
+@pytest.mark.parametrize("kernel,shape,with_bias", _CONV_DIGEST_CASES)
+def test_conv3x3_fwd_bit_exact_digest(kernel, shape, with_bias):
+    import hashlib
+    import json
+    import os
+
+    from fl4health_amd import _C
+    from fl4health_amd.ops.conv import _image_kb32, _pack_fwd
+
+    n, h, w, c, k = shape
+    gen = torch.Generator().manual_seed(0)  # CPU generator: same bits everywhere
+    x = torch.randn(n, h, w, c, generator=gen).to(torch.bfloat16).cuda()
+    weight = (torch.randn(k, c, 3, 3, generator=gen) * 0.05).to(torch.bfloat16).cuda()
+    bias = torch.randn(k, generator=gen).cuda() if with_bias else None
+    w9 = _pack_fwd(weight)
+    if kernel in ("kb32", "kzloop"):
+        assert _C.conv3x3_plan(kernel, *shape)["fits"]
+        run = _C.conv3x3_fwd_kb32 if kernel == "kb32" else _C.conv3x3_fwd_kzloop
+        y = run(x, _image_kb32(w9), bias)
+    else:
+        plan = _C.conv3x3_plan("fwd", *shape)
+        assert plan["fits"] and plan["kernel"] == kernel, plan
+        y = _C.conv3x3_fwd(x, w9, bias)
+    assert y.shape == (n, h, w, k) and y.dtype == torch.bfloat16
+    digest = hashlib.sha256(y.cpu().view(torch.int16).numpy().tobytes()).hexdigest()
+    golden = os.path.join(os.path.dirname(__file__), "golden", "conv3x3_fwd_digests.json")
+    with open(golden) as f:
+        want = json.load(f)
+    key = f"{kernel}:{','.join(map(str, shape))}:{'bias' if with_bias else 'nobias'}"
+    assert digest == want[key], key
+
+
+@requires_gpu
+def test_cdna_conv2d_small_image_falls_back_and_kernel_refuses():
+    """2x2 images pack 32 samples per tile: the kb32 halo (4096 chunks) does
+    not fit its 2304-chunk buffer, so the module must take F.conv2d and the
+    raw binding must refuse before launching."""
+    from fl4health_amd import _C
+    from fl4health_amd.ops.conv import CdnaConv2d, _variant_for
+
+    torch.manual_seed(0)
+    assert _variant_for(2, 64, 64) == "kb32"  # the table alone would adopt it
+    ref = torch.nn.Conv2d(64, 64, 3, padding=1).cuda().to(torch.bfloat16)
+    ours = CdnaConv2d(64, 64, 3, padding=1).cuda().to(torch.bfloat16)
+    ours.load_state_dict(ref.state_dict())
+    x1 = (torch.randn(32, 64, 2, 2, device="cuda") * 0.5).to(torch.bfloat16).contiguous(
+        memory_format=torch.channels_last
+    ).requires_grad_(True)
+    x2 = x1.detach().clone().requires_grad_(True)
+    assert not ours._fast_path(x2)
+    y_ref, y_ours = ref(x1), ours(x2)
+    rel = (y_ours.float() - y_ref.float()).abs().max() / y_ref.float().abs().max().clamp(min=1e-6)
+    assert rel < 3e-2, float(rel)
+    gy = torch.randn_like(y_ref)
+    y_ref.backward(gy)
+    y_ours.backward(gy)
+    r = (x2.grad.float() - x1.grad.float()).abs().max() / x1.grad.float().abs().max().clamp(min=1e-6)
+    assert r < 3e-2, float(r)
+
+    wimg = _C.pack_kb32(ours.weight.detach().contiguous(), False)
+    with pytest.raises(RuntimeError, match="exceeds the LDS buffer"):
+        _C.conv3x3_fwd_kb32(x2.detach().permute(0, 2, 3, 1).contiguous(), wimg, None)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("h,w,c,k", [(32, 32, 64, 64), (16, 16, 128, 128), (16, 16, 64, 128)])
 def test_conv3x3_wrw_kernel_numerics(h, w, c, k):

@@ -268,3 +268,107 @@ def test_bn_v2_geometry_invariants():
         cblocks = (C // 2 + px - 1) // px
         assert cblocks * px >= C // 2  # every pair slot covered
         assert px <= 128
+
+
+_CONV_CHUNK_CAP = {"base": 304 * 8, "glds4": 1792, "glds8": 2752, "kb32": 2304, "kzloop": 1664}
+_CONV_WAVES = {"base": 4, "glds4": 4, "glds8": 8, "kb32": 4, "kzloop": 8}
+_CONV_M_ROWS = {"base": 128, "glds4": 128, "glds8": 256, "kb32": 128, "kzloop": 128}
+_CONV_GRID_CAP = {"glds4": 512, "glds8": 256}
+
+
+def _conv_plan_or_skip():
+    from fl4health_amd.ops import conv
+
+    if not conv.HAS_EXT:
+        pytest.skip("fl4health_amd._C not built")
+    return conv._C.conv3x3_plan
+
+
+def _check_conv_plan(kernel, n, h, w, c, k, p):
+    """What `fits` promises, recomputed here from the kernels' LDS layout
+    (16-byte chunks of 8 bf16; glds writes whole 64-lane groups)."""
+    m = _CONV_M_ROWS[kernel]
+    bh = min(max(m // w, 1), h)
+    sb = min(max(m // (h * w), 1), n)
+    h_groups = -(-h // bh)
+    n_tiles = -(-n // sb) * h_groups
+    where = (kernel, n, h, w, c, k, p)
+    assert (p["BH"], p["SB"], p["h_groups"], p["n_tiles"]) == (bh, sb, h_groups, n_tiles), where
+    assert p["waves"] == _CONV_WAVES[kernel] and p["m_rows"] == m, where
+    chunks = -(-(sb * (bh + 2) * (w + 2) * 8) // 64) * 64
+    assert p["in_chunks"] == chunks <= _CONV_CHUNK_CAP[kernel], where
+    assert sb * bh * w <= m <= p["waves"] * 32, where
+    if kernel in ("kb32", "kzloop"):
+        assert c % 64 == 0 and k % 32 == 0, where
+    if kernel == "kzloop":
+        assert c // 64 <= 2, where
+    if kernel in ("glds4", "glds8"):
+        assert c % 8 == 0 and c <= 64, where
+    kb = {"kb32": 32, "kzloop": None}.get(kernel, 64)
+    grid = (min(n_tiles, _CONV_GRID_CAP.get(kernel, n_tiles)), 1, -(-k // kb) if kb else 1)
+    assert p["grid"] == grid, where
+
+
+def test_conv_plan_fits_implies_lds_and_tile_bounds():
+    plan = _conv_plan_or_skip()
+    pairs = [(64, 64), (128, 64), (64, 128), (192, 64), (512, 512), (24, 64), (96, 80), (64, 48)]
+    n_fit = 0
+    for n in (1, 2, 7, 19, 32, 128):
+        for h in range(1, 35):
+            for w in range(1, 35):
+                for c, k in pairs:
+                    fitting = []
+                    for kernel in ("glds8", "glds4", "base", "kb32", "kzloop"):
+                        p = plan(kernel, n, h, w, c, k)
+                        assert p["kernel"] == kernel
+                        if p["fits"]:
+                            assert p["reason"] == ""
+                            _check_conv_plan(kernel, n, h, w, c, k, p)
+                            fitting.append(kernel)
+                        else:
+                            assert p["reason"]
+                    # conv3x3_fwd: first of glds8, glds4, base that fits
+                    auto = plan("fwd", n, h, w, c, k)
+                    first = next((x for x in fitting if x in ("glds8", "glds4", "base")), None)
+                    assert auto["fits"] == (first is not None)
+                    if first:
+                        assert auto == plan(first, n, h, w, c, k)
+                    n_fit += len(fitting)
+    assert n_fit > 10000  # the sweep is not vacuous
+
+
+def test_conv_plan_known_shapes():
+    plan = _conv_plan_or_skip()
+    # adopted / tested shapes keep today's geometry: (kernel, N,H,W,C,K) -> (BH, SB)
+    must_fit = {
+        ("kb32", 128, 4, 4, 512, 512): (4, 8),
+        ("kb32", 128, 8, 8, 128, 128): (8, 2),
+        ("kzloop", 128, 16, 16, 128, 64): (8, 1),
+        ("kzloop", 128, 16, 16, 64, 128): (8, 1),
+        ("kzloop", 128, 8, 8, 128, 128): (8, 2),
+        ("glds8", 128, 32, 32, 64, 64): (8, 1),
+        ("glds4", 128, 8, 8, 64, 64): (8, 2),
+        ("base", 4, 16, 16, 96, 80): (8, 1),
+    }
+    for (kernel, *shape), geom in must_fit.items():
+        p = plan(kernel, *shape)
+        assert p["fits"], (kernel, shape, p)
+        assert (p["BH"], p["SB"]) == geom, (kernel, shape, p)
+        _check_conv_plan(kernel, *shape, p)
+    assert plan("fwd", 128, 32, 32, 64, 64)["kernel"] == "glds8"
+    assert plan("fwd", 128, 8, 8, 64, 64)["kernel"] == "glds4"
+    assert plan("fwd", 4, 16, 16, 96, 80)["kernel"] == "base"
+    must_not_fit = [
+        ("kb32", 32, 2, 2, 64, 64),   # 32 packed samples: 4096 chunks vs 2304
+        ("kb32", 32, 3, 3, 64, 64),
+        ("kb32", 32, 2, 4, 64, 64),
+        ("kzloop", 128, 16, 16, 192, 64),  # three resident c-chunks
+        ("kzloop", 128, 32, 32, 128, 128),
+        ("base", 32, 2, 2, 128, 128),  # 512 positions vs 304
+    ] + [(kern, n, h, 129, 64, 64) for kern in ("fwd", "base", "glds4", "glds8", "kb32", "kzloop")
+         for n, h in ((1, 1), (2, 4))]
+    for kernel, *shape in must_not_fit:
+        p = plan(kernel, *shape)
+        assert not p["fits"] and p["reason"], (kernel, shape, p)
+    with pytest.raises(RuntimeError):
+        plan("kzloop4", 1, 1, 1, 64, 64)

@@ -14,24 +14,7 @@ import time
 import torch
 
 from fl4health_amd import _C
-
-
-def pack_weight(w: torch.Tensor) -> torch.Tensor:
-    """torch conv weight [K, C, 3, 3] -> [9, C, K] taps-major."""
-    return w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).contiguous()
-
-
-def pack_weight_kb32(w: torch.Tensor) -> torch.Tensor:
-    """[K, C, 3, 3] -> [K/32, C/64, 9, 32, 64] LDS-image slabs, bank-swizzled:
-    rows with kk bit 2 set get channel bit 4 XORed (matches conv_swz on the
-    read side — glds stages the image verbatim, so the swizzle lives here)."""
-    k, c = w.shape[0], w.shape[1]
-    w9 = w.permute(2, 3, 1, 0).reshape(9, c, k)  # [tap, c, k]
-    img = w9.reshape(9, c // 64, 64, k // 32, 32).permute(3, 1, 0, 4, 2).contiguous()
-    kk_mask = (torch.arange(32, device=w.device) >> 2) & 1 == 1
-    cc_swz = torch.arange(64, device=w.device) ^ 16
-    img[:, :, :, kk_mask, :] = img[:, :, :, kk_mask, :][..., cc_swz]
-    return img
+from fl4health_amd.ops.conv import _image_kb32, _pack_fwd
 
 
 def bench(fn, iters):
@@ -59,7 +42,7 @@ def run_shape(n, h, w, c, k, iters=100):
     line = f"N{n} {h}x{w} C{c}->K{k}: MIOpen {t_miopen:.3f} ms ({flops / t_miopen / 1e9:.0f} TF)"
     ok = True
 
-    wp = pack_weight(weight)
+    wp = _pack_fwd(weight)
     out = _C.conv3x3_fwd(x_nhwc, wp, None).permute(0, 3, 1, 2)
     rel = float(((out.float() - ref.float()).abs().max() / refmax))
     okd = rel < 2e-2
@@ -67,19 +50,16 @@ def run_shape(n, h, w, c, k, iters=100):
     t = bench(lambda: _C.conv3x3_fwd(x_nhwc, wp, None), iters)
     line += f" | dispatch {t:.3f} ms ({flops / t / 1e9:.0f} TF) {t_miopen / t:.2f}x{'' if okd else ' FAIL rel=%.4f' % rel}"
 
-    if c % 64 == 0 and k % 32 == 0:
-        wimg = pack_weight_kb32(weight)
+    if _C.conv3x3_plan("kb32", n, h, w, c, k)["fits"]:
+        wimg = _image_kb32(wp)
         out2 = _C.conv3x3_fwd_kb32(x_nhwc, wimg, None).permute(0, 3, 1, 2)
         rel2 = float(((out2.float() - ref.float()).abs().max() / refmax))
         ok2 = rel2 < 2e-2
         ok &= ok2
         t2 = bench(lambda: _C.conv3x3_fwd_kb32(x_nhwc, wimg, None), iters)
         line += f" | kb32 {t2:.3f} ms ({flops / t2 / 1e9:.0f} TF) {t_miopen / t2:.2f}x{'' if ok2 else ' FAIL rel=%.4f' % rel2}"
-        # variant D gate: all input chunks + 2 weight slabs resident
-        bh = min(max(128 // w, 1), h)
-        sb = max(128 // (h * w), 1)
-        in_chunks = sb * (bh + 2) * (w + 2) * 8
-        if c // 64 <= 2 and in_chunks + 63 <= 1664 and k >= 64:
+        # variant D: all input chunks + 2 weight slabs resident
+        if _C.conv3x3_plan("kzloop", n, h, w, c, k)["fits"] and k >= 64:
             out3 = _C.conv3x3_fwd_kzloop(x_nhwc, wimg, None).permute(0, 3, 1, 2)
             rel3 = float(((out3.float() - ref.float()).abs().max() / refmax))
             ok3 = rel3 < 2e-2
