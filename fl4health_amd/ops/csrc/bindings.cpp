@@ -29,6 +29,9 @@ void launch_clip_rowsum_noise(const float*, const float*, float*, float, float, 
 void launch_confusion(const int64_t*, const int64_t*, unsigned long long*, int, int64_t,
                       hipStream_t);
 void launch_weighted_sum_rows(const float*, const float*, float*, int, int64_t, hipStream_t);
+void launch_rank_mean_rows(const float* const*, int, float*, int, int, int64_t, int, hipStream_t);
+int pairwise_sqdist_num_slots(int, int64_t);
+void launch_pairwise_sqdist_rows(const float* const*, int, double*, double*, int64_t, hipStream_t);
 void launch_bn_fwd(const void*, void*, float*, float*, float*, const float*, const float*, float*,
                    float*, int64_t*, float, float, int64_t, int, int, int, int, const void*,
                    hipStream_t);
@@ -583,6 +586,52 @@ torch::Tensor mkmmd_backward(torch::Tensor d, torch::Tensor gammas, torch::Tenso
   return dd;
 }
 
+// Robust aggregation (robust_ops.hip): K separate fp32 rows, 2 <= K <= 64.
+// Returns the row pointers; `aligned16` reports whether all are 16-byte aligned.
+std::vector<const float*> robust_row_ptrs(const std::vector<torch::Tensor>& rows, bool* aligned16) {
+  const int64_t K = (int64_t)rows.size();
+  TORCH_CHECK(K >= 2 && K <= 64, "rows must hold 2..64 tensors, got ", K);
+  std::vector<const float*> ptrs((size_t)K);
+  *aligned16 = true;
+  for (int64_t k = 0; k < K; ++k) {
+    check_f32(rows[k], "rows[k]");
+    TORCH_CHECK(rows[k].dim() == 1, "rows[k] must be 1-D");
+    TORCH_CHECK(rows[k].numel() == rows[0].numel(), "rows must have the same length");
+    TORCH_CHECK(rows[k].device() == rows[0].device(), "rows must share one device");
+    ptrs[(size_t)k] = rows[k].data_ptr<float>();
+    if (reinterpret_cast<uintptr_t>(ptrs[(size_t)k]) % 16 != 0) *aligned16 = false;
+  }
+  return ptrs;
+}
+
+torch::Tensor rank_mean_rows(std::vector<torch::Tensor> rows, int64_t lo, int64_t hi) {
+  bool aligned16 = true;
+  auto ptrs = robust_row_ptrs(rows, &aligned16);
+  const int K = (int)rows.size();
+  TORCH_CHECK(0 <= lo && lo < hi && hi <= K, "need 0 <= lo < hi <= K");
+  const int64_t n = rows[0].numel();
+  auto out = torch::empty({n}, rows[0].options());
+  if (n == 0) return out;
+  if (reinterpret_cast<uintptr_t>(out.data_ptr<float>()) % 16 != 0) aligned16 = false;
+  launch_rank_mean_rows(ptrs.data(), K, out.data_ptr<float>(), (int)lo, (int)hi, n,
+                        aligned16 ? 1 : 0, stream());
+  return out;
+}
+
+torch::Tensor pairwise_sqdist_rows(std::vector<torch::Tensor> rows) {
+  bool aligned16 = true;
+  auto ptrs = robust_row_ptrs(rows, &aligned16);
+  const int K = (int)rows.size();
+  const int64_t n = rows[0].numel();
+  auto opts = rows[0].options().dtype(torch::kFloat64);
+  const int slots = pairwise_sqdist_num_slots(K, n);
+  auto partial = torch::empty({(int64_t)slots * K * K}, opts);
+  auto out = torch::empty({K, K}, opts);
+  launch_pairwise_sqdist_rows(ptrs.data(), K, partial.data_ptr<double>(), out.data_ptr<double>(),
+                              n, stream());
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -624,4 +673,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("in3d_bwd", &in3d_bwd, "fused InstanceNorm3d + LeakyReLU backward");
   m.def("mkmmd_sums", &mkmmd_sums, "per-bandwidth Gaussian kernel sums over a Gram");
   m.def("mkmmd_backward", &mkmmd_backward, "dL/dGram for mkmmd_sums");
+  m.def("rank_mean_rows", &rank_mean_rows,
+        "per-column mean of ranks lo..hi-1 over K separate rows (NaN sorts last)");
+  m.def("pairwise_sqdist_rows", &pairwise_sqdist_rows,
+        "D[i][j] = sum_c (x_i[c]-x_j[c])^2 over K separate rows, fp64 [K, K]");
 }

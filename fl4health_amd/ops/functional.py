@@ -304,6 +304,69 @@ def weighted_sum_rows(stack: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return (w.unsqueeze(1) * stack).sum(dim=0)
 
 
+ROBUST_MAX_ROWS = 64  # the row-pointer kernel-argument struct holds 64 rows
+
+
+def _flat_rows(rows: list[torch.Tensor], op: str) -> list[torch.Tensor]:
+    if len(rows) < 2:
+        raise ValueError(f"{op} needs at least 2 rows, got {len(rows)}")
+    flat = [r.reshape(-1) for r in rows]
+    for r in flat:
+        if r.dtype != torch.float32:
+            raise ValueError(f"{op} rows must be fp32, got {r.dtype}")
+        if r.numel() != flat[0].numel() or r.device != flat[0].device:
+            raise ValueError(f"{op} rows must have one length and one device")
+    return flat
+
+
+def _rank_mean_rows_torch(flat: list[torch.Tensor], lo: int, hi: int) -> torch.Tensor:
+    # torch.sort orders -inf < finite < +inf < NaN; ranks are then added in
+    # ascending order with sequential fp32 adds, as the kernel does
+    ordered = torch.sort(torch.stack(flat), dim=0).values
+    acc = ordered[lo].clone()
+    for r in range(lo + 1, hi):
+        acc += ordered[r]
+    return acc / float(hi - lo)
+
+
+def rank_mean_rows(rows: list[torch.Tensor], lo: int, hi: int) -> torch.Tensor:
+    """Per column of K equally long fp32 rows: mean of the values of ascending
+    ranks lo..hi-1 (NaN ranks last). Median: (K//2, K//2+1) for odd K,
+    (K/2-1, K/2+1) for even K; b-trimmed mean: (b, K-b).
+
+    GPU with K <= 64: one register-sorting HIP kernel over the separate rows
+    (no [K, n] stack). CPU, or K > 64 on either device: torch.sort composition.
+    """
+    flat = _flat_rows(rows, "rank_mean_rows")
+    k = len(flat)
+    if not (0 <= lo < hi <= k):
+        raise ValueError(f"rank_mean_rows needs 0 <= lo < hi <= K, got lo={lo} hi={hi} K={k}")
+    if flat[0].is_cuda and k <= ROBUST_MAX_ROWS:
+        _require_ext("rank_mean_rows")
+        return _C.rank_mean_rows(flat, lo, hi)
+    return _rank_mean_rows_torch(flat, lo, hi)
+
+
+def _pairwise_sqdist_rows_torch(flat: list[torch.Tensor]) -> torch.Tensor:
+    x = torch.stack(flat).double()
+    return torch.stack([((x - x[i]) ** 2).sum(dim=1) for i in range(x.shape[0])])
+
+
+def pairwise_sqdist_rows(rows: list[torch.Tensor]) -> torch.Tensor:
+    """D[i][j] = sum_c (x_i[c] - x_j[c])^2 as an fp64 [K, K] tensor, computed
+    from the differences (client models differ by small updates on large
+    weights, where the Gram form cancels).
+
+    GPU with K <= 64: one-pass HIP kernel, deterministic, exactly symmetric.
+    CPU, or K > 64 on either device: fp64 torch composition.
+    """
+    flat = _flat_rows(rows, "pairwise_sqdist_rows")
+    if flat[0].is_cuda and len(flat) <= ROBUST_MAX_ROWS:
+        _require_ext("pairwise_sqdist_rows")
+        return _C.pairwise_sqdist_rows(flat)
+    return _pairwise_sqdist_rows_torch(flat)
+
+
 def noise_multiplier_sigma(noise_multiplier: float, clip_bound: float, num: int) -> float:
     """Std-dev of per-coordinate Gaussian noise for a summed, clipped aggregate."""
     return noise_multiplier * clip_bound / max(num, 1) * math.sqrt(1.0)

@@ -12,6 +12,9 @@ from fl4health_amd.strategies.fedavg_sparse_coo_tensor import FedAvgSparseCooTen
 from fl4health_amd.strategies.fedpm import FedPm
 from fl4health_amd.strategies.fedpca import FedPCA
 from fl4health_amd.strategies.model_merge_strategy import ModelMergeStrategy
+from fl4health_amd.strategies.fed_median import FedMedian
+from fl4health_amd.strategies.fed_trimmed_avg import FedTrimmedAvg
+from fl4health_amd.strategies.krum import Krum
 
 __all__ = [
     "Strategy",
@@ -35,4 +38,7 @@ __all__ = [
     "FedPm",
     "FedPCA",
     "ModelMergeStrategy",
+    "FedMedian",
+    "FedTrimmedAvg",
+    "Krum",
 ]

@@ -27,6 +27,7 @@ setup(
                 os.path.join(CSRC, "conv_ops.hip"),
                 os.path.join(CSRC, "contrastive_ops.hip"),
                 os.path.join(CSRC, "in_ops.hip"),
+                os.path.join(CSRC, "robust_ops.hip"),
             ],
             extra_compile_args={
                 # FL4_ASAN=1: host-side AddressSanitizer build of the binding
